@@ -14,6 +14,12 @@ advancing with zamboni).  `--config 2` = configs[1] (4,096 docs x 2k text-only o
 Multi-GPU: one process per GPU (torchrun); documents shard across ranks with no data-path
 collective (weak scaling); rank 0 gathers per-document results with RCCL (torch.distributed
 "nccl").  rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (ops/s, ms_per_step, the
+last step's launches and digests).  `--dump-outputs DIR` also writes what the last timed step
+returned as .npy files.  `--full` adds everything that takes work of its own after the timed
+steps: the CPU oracle baseline and parity check, the roofline figures, capacity percentiles and the
+SnapshotV1 gather and host spot check.
 """
 from __future__ import annotations
 
@@ -58,14 +64,24 @@ def parse():
     ap.add_argument("--seed", type=int, default=0xDEADBEEF)
     ap.add_argument("--cpu-sample-docs", type=int, default=0, help="oracle baseline sample (default: auto)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads (default: every usable core)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the oracle baseline and parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU oracle "
+                         "baseline + parity check, the roofline / per-launch figures, capacity percentiles and the "
+                         "SnapshotV1 gather and host spot check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (rank 0's gathered "
+                         "per-document digests and statuses) as DIR/<name>.npy")
     ap.add_argument("--seg-cap", type=int, default=0, help="first capacity class (default: from the op count)")
     ap.add_argument("--snapshot", action="store_true", help="serialize SnapshotV1 of every doc in each step")
     ap.add_argument("--launch-check", action="store_true",
                     help="rank layout + gather to rank 0 only, no replay (tests the --gpus N launcher on CPU)")
     ap.add_argument("--writers", action="store_true",
                     help="replay every document as one of its writers (local ops + acks, the local-client path)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 and not args.launch_check:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port() -> int:
@@ -259,19 +275,20 @@ def main():
     for i in range(args.steps):
         sn, gathered = step()
         kernel_ms.append(b.stats()["kernel_ms"])
-        # the dominant kernel: the launch that took the longest (config 4: the giant-class launch of
-        # the Zipf tail, not the class that applied the most ops)
-        lis = b.launches()
-        l0 = max(lis, key=lambda li: li["ms"])
-        first_ms.append(l0["ms"])
-        first_ops.append(l0["ops"])
-        dom_class = l0["seg_class"]
-        # the launches of that class share the chip (config 3: the two halves' launches run
-        # concurrently): their ops over the span from the first one's start to the last one's end
-        dom = [li for li in lis if li["seg_class"] == dom_class]
-        cls_span.append(max(li["start_ms"] + li["ms"] for li in dom) - min(li["start_ms"] for li in dom))
-        cls_ops.append(sum(li["ops"] for li in dom))
-        cls_launches.append(len(dom))
+        if args.full:
+            # the dominant kernel: the launch that took the longest (config 4: the giant-class launch of
+            # the Zipf tail, not the class that applied the most ops)
+            lis = b.launches()
+            l0 = max(lis, key=lambda li: li["ms"])
+            first_ms.append(l0["ms"])
+            first_ops.append(l0["ops"])
+            dom_class = l0["seg_class"]
+            # the launches of that class share the chip (config 3: the two halves' launches run
+            # concurrently): their ops over the span from the first one's start to the last one's end
+            dom = [li for li in lis if li["seg_class"] == dom_class]
+            cls_span.append(max(li["start_ms"] + li["ms"] for li in dom) - min(li["start_ms"] for li in dom))
+            cls_ops.append(sum(li["ops"] for li in dom))
+            cls_launches.append(len(dom))
         if with_snap:
             snap_ms.append(sn["device_ms"])
             snap_bytes = sn["bytes"]
@@ -286,8 +303,6 @@ def main():
     if args.writers:  # the metric counts the log's sequenced messages, not the writers' local copies
         ops_done -= n_local
     ops_all = ops_done
-    alg_bytes = b.algorithmic_bytes()
-    alg_all = alg_bytes
     if world > 1:
         dev = "cuda" if backend == "nccl" else "cpu"
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -296,17 +311,8 @@ def main():
         o = torch.tensor([ops_done], device=dev, dtype=torch.int64)
         dist.all_reduce(o, op=dist.ReduceOp.SUM)
         ops_all = int(o.item())
-        a = torch.tensor([alg_bytes], device=dev, dtype=torch.float64)
-        dist.all_reduce(a, op=dist.ReduceOp.SUM)
-        alg_all = float(a.item())
     ranks_gathered = dist.get_world_size() if dist.is_initialized() else 1
-    summaries = None
-    if with_snap:  # the SnapshotV1 bytes themselves to rank 0 (after the timed steps)
-        summaries = gather_summaries(b, torch, dist, world, rank, backend)
 
-    cnt = b.counters()
-    capacity = {f: [int(np.percentile(cnt[f], q)) for q in (50, 99, 100)]
-                for f in ("max_slots", "max_unsettled", "max_blocks", "max_heap")}
     all_ok, not_ok, digest_xor, snap_xor = 0, None, None, None
     if rank == 0:
         all_dig, all_st = gathered[:2]
@@ -315,10 +321,111 @@ def main():
         digest_xor = f"{int(np.bitwise_xor.reduce(all_dig)):016x}"
         if with_snap:
             snap_xor = f"{int(np.bitwise_xor.reduce(gathered[2])):016x}"
+        if args.dump_outputs:
+            dump_outputs(Path(args.dump_outputs), gathered, sn)
     # throughput counts the ops actually applied (a document that stopped early counts only its
     # applied ops); requested_ops_per_step is reported beside it
     value = ops_all * args.steps / t_max
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    snapshot = None
+    if with_snap:
+        avg_snap = sum(snap_ms) / len(snap_ms)
+        snapshot = {"bytes_per_step": int(snap_bytes), "avg_device_ms": round(avg_snap, 3),
+                    "GB_per_s": round(snap_bytes / (avg_snap * 1e-3) / 1e9, 3), "kernel": "mt_snapshot_kernel"}
+    line = {
+        "metric": "sequenced merge-tree ops/sec",
+        "value": round(value, 1),
+        "unit": "ops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * t_max / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic (GPU-generated conflict-farm logs, include/mt_gen.h)",
+        "config": {"workload": ("writer replicas (local ops + acks) of " if args.writers else "") + cfg["workload"],
+                   "docs_per_gpu": n_docs,
+                   "ops_per_doc": n_ops if sizes is None else {"min": int(sizes.min()), "max": int(sizes.max()),
+                                                              "lpt_loads": loads},
+                   "clients": cfg["n_clients"], "max_lag": cfg["max_lag"],
+                   "op_mix": [cfg["pct_insert"], cfg["pct_remove"], 100 - cfg["pct_insert"] - cfg["pct_remove"]],
+                   "parallelism": f"doc-sharded x{world}",
+                   "step": "replay + device digests" + (" + GPU SnapshotV1" if with_snap else "") +
+                           " + gather to rank 0"},
+        "replay_ms_per_step": round(avg_kernel_ms, 3),
+        "launches": b.launches(),
+        "snapshot": snapshot,
+        "docs_ok": all_ok,
+        # writer replicas can stop where the reference's would (a remote insert beside the
+        # replica's own unacked removes: the #1213 family, "MergeTree insert failed");
+        # --full's parity.digest_match compares statuses too
+        "docs_not_ok": not_ok,
+        "digests_gathered": len(gathered[0]) if rank == 0 else None,
+        "ranks_gathered": ranks_gathered,
+        "digest_xor": digest_xor,
+        "snapshot_digest_xor": snap_xor,
+        "ops_applied_per_step": ops_all,
+        "requested_ops_per_step": int(total_ops_step),
+        "lds_bytes_per_doc": st["lds_bytes"],
+        "launches_per_step": st["launches"],
+        "gen_s": round(gen_s, 2),
+    }
+    if args.full:  # every rank: the report's gathers are collective
+        line.update(full_report(locals()))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    b.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, gathered, sn):
+    """--dump-outputs: what the last timed step() returned on rank 0, as float32 .npy files.
+    digests / snapshot_digests: the 64-bit per-document values as four 16-bit limbs (least
+    significant first), each exact in float32; status: the per-document status codes;
+    snapshot_bytes: the SnapshotV1 bytes that step serialized (configs with a snapshot)."""
+    import numpy as np
+
+    def limbs(x):
+        x = np.ascontiguousarray(x).astype(np.uint64)
+        return np.stack([(x >> np.uint64(16 * k)) & np.uint64(0xFFFF) for k in range(4)], axis=1).astype(np.float32)
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "digests.npy", limbs(gathered[0]))
+    np.save(out_dir / "status.npy", np.asarray(gathered[1]).astype(np.float32))
+    if len(gathered) > 2 and gathered[2] is not None:
+        np.save(out_dir / "snapshot_digests.npy", limbs(gathered[2]))
+    if sn is not None:
+        np.save(out_dir / "snapshot_bytes.npy", np.array([sn["bytes"]], np.float64))
+
+
+def full_report(v):
+    """--full: what the headline figure does not need, from main()'s state `v` after the timed steps:
+    the roofline of the dominant kernel, capacity percentiles, the oracle baseline + parity check
+    (unless --no-cpu) and, with a snapshot, the SnapshotV1 gather to rank 0 and the host spot check.
+    Returns the extra keys of the result line."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    args, b, world, rank, backend = v["args"], v["b"], v["world"], v["rank"], v["backend"]
+    n_docs, n_ops, ops_done, t_max = v["n_docs"], v["n_ops"], v["ops_done"], v["t_max"]
+    first_ms, first_ops, cls_span, cls_ops, cls_launches = (v[k] for k in ("first_ms", "first_ops", "cls_span",
+                                                                           "cls_ops", "cls_launches"))
+    alg_bytes = b.algorithmic_bytes()
+    alg_all = alg_bytes
+    if world > 1:
+        a = torch.tensor([alg_bytes], device="cuda" if backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(a, op=dist.ReduceOp.SUM)
+        alg_all = float(a.item())
+    summaries = None
+    if v["with_snap"]:  # the SnapshotV1 bytes themselves to rank 0 (after the timed steps)
+        summaries = gather_summaries(b, torch, dist, world, rank, backend)
+    cnt = b.counters()
+    capacity = {f: [int(np.percentile(cnt[f], q)) for q in (50, 99, 100)]
+                for f in ("max_slots", "max_unsettled", "max_blocks", "max_heap")}
     # roofline of the dominant kernel (the longest launch, mt_replay_kernel_<class>): the algorithmic bytes
     # of the ops it applied (DESIGN.md "Roofline": per-op share of the batch's algorithmic bytes)
     # over its average launch duration (hipEvents on the launch's stream)
@@ -333,7 +440,7 @@ def main():
     class_gbs = alg_per_op * avg_cls_ops / (avg_cls_span * 1e-3) / 1e9
     # the whole step: every rank's algorithmic bytes over the max-over-ranks step time
     step_gbs = alg_all * args.steps / t_max / 1e9
-    kname = f"mt_{'writer' if args.writers else 'replay'}_kernel_{dom_class}"
+    kname = f"mt_{'writer' if args.writers else 'replay'}_kernel_{v['dom_class']}"
     traffic, traffic_src = pmc_traffic(args.config, n_docs, n_ops, kname, ops_per_launch)
     # issue / LDS utilisation over the chip time the class's concurrent launches share
     lds = lds_busy(args.config, n_ops, kname, avg_cls_span, avg_cls_ops)
@@ -341,86 +448,40 @@ def main():
     cpu = None
     parity = None
     if rank == 0 and not args.no_cpu:
-        cpu, parity = cpu_baseline(b, fa, n_docs, args, writer_log)
-    snapshot = None
-    if with_snap:
-        avg_snap = sum(snap_ms) / len(snap_ms)
-        snapshot = {"bytes_per_step": int(snap_bytes), "avg_device_ms": round(avg_snap, 3),
-                    "GB_per_s": round(snap_bytes / (avg_snap * 1e-3) / 1e9, 3), "kernel": "mt_snapshot_kernel",
-                    "summaries_gathered": summaries}
+        cpu, parity = cpu_baseline(b, v["fa"], n_docs, args, v["writer_log"])
+    snapshot = v["snapshot"]
+    if snapshot is not None:
+        snapshot = dict(snapshot, summaries_gathered=summaries)
         if rank == 0:  # spot check: GPU blobs == host serializer on a sample
             sample = range(0, n_docs, max(1, n_docs // 64))
             snapshot["host_match"] = sum(b.doc(d).snapshot_v1(device=True) == b.doc(d).snapshot_v1() for d in sample)
             snapshot["checked"] = len(sample)
-
-    if rank == 0:
-        line = {
-            "metric": "sequenced merge-tree ops/sec",
-            "value": round(value, 1),
-            "unit": "ops/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * t_max / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic (GPU-generated conflict-farm logs, include/mt_gen.h)",
-            "config": {"workload": ("writer replicas (local ops + acks) of " if args.writers else "") + cfg["workload"],
-                       "docs_per_gpu": n_docs,
-                       "ops_per_doc": n_ops if sizes is None else {"min": int(sizes.min()), "max": int(sizes.max()),
-                                                                  "lpt_loads": loads},
-                       "clients": cfg["n_clients"], "max_lag": cfg["max_lag"],
-                       "op_mix": [cfg["pct_insert"], cfg["pct_remove"], 100 - cfg["pct_insert"] - cfg["pct_remove"]],
-                       "parallelism": f"doc-sharded x{world}",
-                       "step": "replay + device digests" + (" + GPU SnapshotV1" if with_snap else "") +
-                               " + gather to rank 0"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "traffic_per": "launch (PMC HBM bytes per op of this kernel x ops_per_launch)",
-                         "kernel": kname, "avg_launch_ms": round(avg_first_ms, 3),
-                         "algorithmic_bytes_per_launch": int(first_bytes),
-                         "algorithmic_bytes_per_op": round(alg_per_op, 2),
-                         "algorithmic_bytes_formula": "32 B/op record + 2 B/inserted code unit + 8 B/prop record "
-                                                      "+ 32 B/final table entry (DESIGN.md §5)",
-                         "ops_per_launch": int(ops_per_launch),
-                         "class_window": {"launches": round(sum(cls_launches) / len(cls_launches), 2),
-                                          "span_ms": round(avg_cls_span, 3), "ops": int(avg_cls_ops),
-                                          "achieved": round(class_gbs, 3),
-                                          "frac": round(class_gbs / HBM_PEAK_GBS, 6)},
-                         "step": {"achieved": round(step_gbs, 3), "frac": round(step_gbs / HBM_PEAK_GBS, 6),
-                                  "algorithmic_bytes_per_step": int(alg_all)},
-                         "utilisation_window": "issue_frac / lds_busy: the class window's ops over its span x the chip",
-                         "lds_busy": lds,
-                         "issue_frac": issue["frac"] if issue else None,
-                         "issue": issue},
-            "replay_ms_per_step": round(avg_kernel_ms, 3),
-            "launches": b.launches(),
-            "cpu_baseline": cpu,
-            "parity": parity,
-            "snapshot": snapshot,
-            "docs_ok": all_ok,
-            # writer replicas can stop where the reference's would (a remote insert beside the
-            # replica's own unacked removes: the #1213 family, "MergeTree insert failed");
-            # parity.digest_match compares statuses too
-            "docs_not_ok": not_ok,
-            "digests_gathered": len(gathered[0]) if rank == 0 else None,
-            "ranks_gathered": ranks_gathered,
-            "digest_xor": digest_xor,
-            "snapshot_digest_xor": snap_xor,
-            "ops_applied_per_step": ops_all,
-            "requested_ops_per_step": int(total_ops_step),
-            "lds_bytes_per_doc": st["lds_bytes"],
-            "launches_per_step": st["launches"],
-            "capacity_p50_p99_max": capacity,
-            "gen_s": round(gen_s, 2),
-        }
-        print(json.dumps(line), flush=True)
-    b.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return {
+        "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic,
+                     "traffic_source": traffic_src,
+                     "traffic_per": "launch (PMC HBM bytes per op of this kernel x ops_per_launch)",
+                     "kernel": kname, "avg_launch_ms": round(avg_first_ms, 3),
+                     "algorithmic_bytes_per_launch": int(first_bytes),
+                     "algorithmic_bytes_per_op": round(alg_per_op, 2),
+                     "algorithmic_bytes_formula": "32 B/op record + 2 B/inserted code unit + 8 B/prop record "
+                                                  "+ 32 B/final table entry (DESIGN.md §5)",
+                     "ops_per_launch": int(ops_per_launch),
+                     "class_window": {"launches": round(sum(cls_launches) / len(cls_launches), 2),
+                                      "span_ms": round(avg_cls_span, 3), "ops": int(avg_cls_ops),
+                                      "achieved": round(class_gbs, 3),
+                                      "frac": round(class_gbs / HBM_PEAK_GBS, 6)},
+                     "step": {"achieved": round(step_gbs, 3), "frac": round(step_gbs / HBM_PEAK_GBS, 6),
+                              "algorithmic_bytes_per_step": int(alg_all)},
+                     "utilisation_window": "issue_frac / lds_busy: the class window's ops over its span x the chip",
+                     "lds_busy": lds,
+                     "issue_frac": issue["frac"] if issue else None,
+                     "issue": issue},
+        "cpu_baseline": cpu,
+        "parity": parity,
+        "snapshot": snapshot,
+        "capacity_p50_p99_max": capacity,
+    }
 
 
 def pmc_traffic(config, n_docs, n_ops, kernel, ops_per_launch):

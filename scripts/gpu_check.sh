@@ -16,10 +16,10 @@ for step in "$@"; do
   case "$step" in
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v -s --timeout 200 --timeout-method thread -p no:cacheprovider ;;
     smoke) run smoke 300 python -u __graft_entry__.py smoke ;;
-    bench) run bench 900 python -u bench.py --steps 3 --warmup 1 ;;
-    benchfinal) run benchfinal 600 python -u bench.py --steps 20 --warmup 5 ;;
-    bench2) run bench2 600 python -u bench.py --config 2 --steps 3 --warmup 1 ;;
-    bench3) run bench3 900 python -u bench.py --config 3 --docs 2048 --steps 2 --warmup 1 ;;
+    bench) run bench 900 python -u bench.py --steps 3 --warmup 1 --full ;;
+    benchfinal) run benchfinal 600 python -u bench.py --steps 20 --warmup 5 --full ;;
+    bench2) run bench2 600 python -u bench.py --config 2 --steps 3 --warmup 1 --full ;;
+    bench3) run bench3 900 python -u bench.py --config 3 --docs 2048 --steps 2 --warmup 1 --full ;;
     gianttests) run gianttests 600 python -u -m pytest tests/test_gpu_parity.py -k "giant or 16_bit or wide_collab or hbm_class or escalation" -x -v -s --timeout 300 --timeout-method thread -p no:cacheprovider ;;
     giant1m) run giant1m 600 python -u -m pytest tests/test_gpu_parity.py -k "million_segments" -x -v -s --timeout 500 --timeout-method thread -p no:cacheprovider ;;
     hbmphases) run hbmphases 600 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_prof.so python -u tools/hbm_phases.py 100000 8 ;;
@@ -42,15 +42,15 @@ for step in "$@"; do
     b3s_var) run b3s_var 600 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_var.so python -u bench.py --config 3 --docs 8192 --steps 2 --warmup 1 --no-cpu ;;
     b3full) run b3full 600 python -u bench.py --steps 3 --warmup 1 --no-cpu ;;
     b3full_var) run b3full_var 600 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_var.so python -u bench.py --steps 3 --warmup 1 --no-cpu ;;
-    c2) run c2 600 python -u bench.py --config 2 --steps 5 --warmup 2 ;;
+    c2) run c2 600 python -u bench.py --config 2 --steps 5 --warmup 2 --full ;;
     earlytest) run earlytest 300 python -u -m pytest tests/test_gpu_parity.py -k "early_escalation or several_classes or escalation" -x -v --timeout 200 --timeout-method thread -p no:cacheprovider ;;
-    c2w) run c2w 600 python -u bench.py --config 2 --writers --steps 3 --warmup 1 ;;
+    c2w) run c2w 600 python -u bench.py --config 2 --writers --steps 3 --warmup 1 --full ;;
     c2wnsp) run c2wnsp 600 env MT_EARLY_SETPRIO=0 python -u bench.py --config 2 --writers --steps 3 --warmup 1 --no-cpu ;;
     c2wne) run c2wne 600 env MT_EARLY_ESCALATION=0 python -u bench.py --config 2 --writers --steps 3 --warmup 1 --no-cpu ;;
-    c5ne) run c5ne 900 env MT_EARLY_ESCALATION=0 python -u bench.py --config 5 --steps 3 --warmup 1 --no-cpu ;;
-    c5) run c5 900 python -u bench.py --config 5 --steps 3 --warmup 1 ;;
+    c5ne) run c5ne 900 env MT_EARLY_ESCALATION=0 python -u bench.py --config 5 --steps 3 --warmup 1 --full --no-cpu ;;
+    c5) run c5 900 python -u bench.py --config 5 --steps 3 --warmup 1 --full ;;
     fullpar) run fullpar 900 python -u tools/full_parity.py 65536 8192 gpurun_out/full_parity_config3.json ;;
-    c4) run c4 900 python -u bench.py --config 4 --steps 1 --warmup 0 ;;
+    c4) run c4 900 python -u bench.py --config 4 --steps 1 --warmup 0 --full ;;
     b3s_old) run b3s_old 600 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_old.so python -u bench.py --config 3 --docs 8192 --steps 2 --warmup 1 --no-cpu ;;
     giantrate) run giantrate 600 python -u tools/hbm_phases.py 100000 8 2000000 ;;
     giantrate_nopf) run giantrate_nopf 600 env MT_GIANT_PREFETCH=0 python -u tools/hbm_phases.py 100000 8 2000000 ;;
@@ -69,17 +69,17 @@ for step in "$@"; do
     full3) run full3 900 python -u bench.py --config 3 --docs 65536 --steps 1 --warmup 0 --no-cpu ;;
     full3p) run full3p 900 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_prof.so python -u bench.py --config 3 --docs 8192 --steps 1 --warmup 0 --no-cpu ;;
     snaptests) run snaptests 300 python -u -m pytest tests/test_gpu_snapshot.py -x -v --timeout 120 --timeout-method thread -p no:cacheprovider ;;
-    benchsnap) run benchsnap 600 python -u bench.py --snapshot --steps 3 --warmup 1 --no-cpu ;;
-    bench5) run bench5 900 python -u bench.py --config 5 --steps 2 --warmup 1 --no-cpu ;;
+    benchsnap) run benchsnap 600 python -u bench.py --snapshot --steps 3 --warmup 1 --full --no-cpu ;;
+    bench5) run bench5 900 python -u bench.py --config 5 --steps 2 --warmup 1 --full --no-cpu ;;
     profsnap) run profsnap 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profsnap -o run -- python3 -u bench.py --config 5 --docs 32768 --steps 2 --warmup 1 --no-cpu ;;
-    benchw2) run benchw2 600 python -u bench.py --config 2 --writers --steps 3 --warmup 1 ;;
-    benchw3) run benchw3 900 python -u bench.py --config 3 --docs 8192 --writers --steps 2 --warmup 1 ;;
+    benchw2) run benchw2 600 python -u bench.py --config 2 --writers --steps 3 --warmup 1 --full ;;
+    benchw3) run benchw3 900 python -u bench.py --config 3 --docs 8192 --writers --steps 2 --warmup 1 --full ;;
     bench2o) run bench2o 600 python -u bench.py --config 2 --steps 3 --warmup 1 --no-cpu ;;
     bench3s_wpe4) run bench3s_wpe4 900 env FLUIDFRAMEWORK_AMD_LIB=fluidframework_amd/libmtreplay_wpe4.so python -u bench.py --config 3 --docs 8192 --steps 2 --warmup 1 --no-cpu ;;
     bench3s) run bench3s 900 python -u bench.py --config 3 --docs 8192 --steps 2 --warmup 1 --no-cpu ;;
     writertests) run writertests 600 python -u -m pytest tests/test_gpu_writer.py tests/test_node_host.py -m gpu -x -v --timeout 200 --timeout-method thread -p no:cacheprovider ;;
     bench4s) run bench4s 600 python -u bench.py --config 4 --docs 4096 --ops 20000 --steps 1 --warmup 0 --no-cpu ;;
-    bench4) run bench4 1100 python -u bench.py --config 4 --steps 1 --warmup 0 ;;
+    bench4) run bench4 1100 python -u bench.py --config 4 --steps 1 --warmup 0 --full ;;
     loadtests) run loadtests 300 python -u -m pytest tests/test_gpu_snapshot_load.py -x -v --timeout 120 --timeout-method thread -p no:cacheprovider ;;
     cap848) run cap848 600 python -u bench.py --steps 1 --warmup 0 --no-cpu --seg-cap 848 ;;
     cap456) run cap456 600 python -u bench.py --steps 1 --warmup 0 --no-cpu --seg-cap 456 ;;
